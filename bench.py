@@ -1,6 +1,12 @@
 """Benchmark: feature-timesteps/sec (fwd+bwd) of the tri-modal MMCTransformer training step.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline figure needs: it sets up, warms up, times the K steps, writes
+the last step's outputs if ``--dump-outputs DIR`` is given (below) and prints the result line.
+``--full`` adds every other measurement and check described here to the same run and the same line:
+the per-kernel `roofline` (and `comm` at N > 1), `param_checksums`, `fresh_batch`, `parity_mode` and
+`cpu_baseline`.
 
 With ``--gpus N`` (N > 1) and no ``WORLD_SIZE`` in the environment, this process starts the N ranks
 itself — ``python -m torch.distributed.run --nproc-per-node N ... bench.py`` as a CHILD process,
@@ -15,12 +21,20 @@ softmax and accumulators), dropout 0.1 active.  One step = forward + losses + ba
 all-reduce over RCCL (N > 1) + fused Adam (lr 1e-3, weight decay 1e-4).  Synthetic seeded inputs
 with the feature statistics of SURVEY §8d, random-init weights (seed 1234); inputs resident in HBM.
 
+``--dump-outputs DIR`` writes what the last timed step handed back, right after the timed region, as
+float32 ``DIR/<name>.npy`` (rank 0): ``loss`` (the step's loss), and ``params`` / ``grads``, the updated
+parameters and the gradients of that step at a fixed seeded sample of DUMP_SAMPLE positions of the
+flat buffers (the whole buffers are 2 x 210 MB).  Inputs, weights and dropout streams are seeded, so the
+same arguments give the same step from run to run and two builds can be compared output for output.
+
 Prints ONE JSON line (rank 0).  At N = 1 the timed steps replay the step captured as a HIP graph
 (repurpose_amd/graph.py); at N > 1 they run the eager DP step (the bucketed RCCL all-reduces issued
 from the backward, as DDP does) unless ``--graph on`` asks for the captured DP step (its all-reduces
 captured with the step: run on one rank only so far, so it stays opt-in).  ``ms_per_step`` is the MEAN
 over the K timed steps (one barrier-bracketed region: a replay loop cannot be split per step without
-syncs).  Every rank reports an exact checksum of its parameters after its last step
+syncs).
+
+With ``--full`` only: every rank reports an exact checksum of its parameters after its last step
 (``param_checksums``): data parallelism must leave them identical.  `roofline` is the dominant
 kernel's achieved MFMA rate measured with HIP events on its launch stream over eager steps of the same
 workload right after the timed region; `cpu_baseline` is the oracle (stock torch CPU modules, fp32, the reference's own
@@ -194,19 +208,26 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None, help="ranks (one per GPU); default WORLD_SIZE or 1")
     ap.add_argument("--dry-run", action="store_true", help="print the N-rank launcher command and exit")
-    ap.add_argument("--no-parity-mode", action="store_true", help="skip the fp32 parity-mode replay (N = 1)")
-    ap.add_argument("--no-fresh-batch", action="store_true", help="skip the fresh-batch loop (N = 1)")
-    ap.add_argument("--fresh-batch", action="store_true", help="also run the fresh-batch loop at N > 1")
+    ap.add_argument("--no-parity-mode", action="store_true", help="--full: skip the fp32 parity-mode replay (N = 1)")
+    ap.add_argument("--no-fresh-batch", action="store_true", help="--full: skip the fresh-batch loop (N = 1)")
+    ap.add_argument("--fresh-batch", action="store_true", help="--full: also run the fresh-batch loop at N > 1")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement and check: per-kernel roofline (and comm at N > 1), "
+                         "parameter checksums, the fresh-batch loop, the fp32 parity mode and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (loss, sampled parameters and gradients) as "
+                         "float32 DIR/<name>.npy")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--seq-len", type=int, default=2048)
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--dtype", default="bf16")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--graph", default="auto", choices=["auto", "on", "off"],
                     help="replay the step as a captured HIP graph (auto: at N = 1 only; on: also the DP step "
                          "with its RCCL all-reduces captured)")
-    ap.add_argument("--roofline-kernel", default="attn_bwd_dkdv", choices=list(KERNEL_FLOPS))
+    ap.add_argument("--roofline-kernel", default="attn_bwd_dkdv", choices=list(KERNEL_FLOPS),
+                    help="--full: the kernel the roofline names")
     ap.add_argument("--no-adam-overlap", action="store_true",
                     help="N > 1: one whole-buffer Adam after the exchange instead of one per all-reduce bucket "
                          "right after its wait (FusedAdam.overlap_with)")
@@ -240,7 +261,6 @@ def main():
             dist.init_process_group(backend, timeout=tmo)
     dev = torch.device("cuda", gpu if dp else 0)
 
-    from repurpose_amd import kernels as K
     from repurpose_amd.MMCTransformer import MMCTransformer
     from repurpose_amd.distributed import GradAllReducer
     from repurpose_amd.optim import FusedAdam
@@ -283,7 +303,9 @@ def main():
     else:
         step = eager_step
 
-    for _ in range(max(args.warmup, 2 if use_graph else 0)):
+    # a captured step runs eagerly once, then captures each input set's graph at that set's first replay:
+    # at least that many warm-up steps, so that the K timed steps are K replays and nothing else
+    for _ in range(max(args.warmup, 1 + len(runner.sets) if use_graph else 0)):
         step()
     torch.cuda.synchronize()
     if dp:
@@ -305,6 +327,71 @@ def main():
         dist.all_gather(allt, t)
         per_rank = [float(x.item()) for x in allt]
         elapsed = max(per_rank)
+    value = world * B * T * args.steps / elapsed
+    res = {"metric": METRIC, "value": value,
+           "unit": "feature-timesteps/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+           "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+           "vs_baseline": None, "dtype": args.dtype, "data": "synthetic (seeded, SURVEY §8d statistics)",
+           "config": {"workload": f"tri-modal MMCTransformer L=16 d=512 H=8 dff=2048, T={T}, B={B}/GPU, "
+                                  f"train step fwd+focal+bwd+allreduce+Adam",
+                      "model": "MMCTransformer (configs/Repurpose.yaml)", "global_batch": B * world,
+                      "seq_len": T, "parallelism": f"dp{world}"},
+           "loss": loss_val, "ranks_seen": ranks_seen,
+           "timing": "mean ms over the K timed steps (barrier + synchronize on both sides, max over ranks)",
+           "rank_ms_per_step": [x / args.steps * 1e3 for x in per_rank],
+           "rank_spread_ms": (max(per_rank) - min(per_rank)) / args.steps * 1e3,
+           "execution": ("hip-graph replay of the captured step" + (" (RCCL all-reduces captured)" if dp else ""))
+           if use_graph else "eager (per-launch)", "full": args.full}
+    # the last timed step's outputs, before anything else touches the parameters or the gradients
+    if args.dump_outputs and rank == 0:
+        res["outputs"] = dump_outputs(args.dump_outputs, model, loss)
+    if args.full:
+        full_report(args, res, model, opt, reducer, runner, eager_step, batch, dev, rank, world, dp, ranks_seen)
+        # the fp32 parity mode needs the memory of the bf16 step's model, graph pool and moments
+        if world == 1 and not args.no_parity_mode and args.dtype != "fp32":
+            del runner, model, opt, batch, eager_step, step
+            torch.cuda.empty_cache()
+            res["parity_mode"] = parity_mode(B, T, dev, rank)
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            res["cpu_baseline"] = cpu_baseline(T)
+            res["speedup_vs_cpu"] = value / res["cpu_baseline"]["value"]
+    if rank == 0:
+        print(json.dumps(res), flush=True)
+    if dp:
+        dist.destroy_process_group()
+
+
+DUMP_SAMPLE = 1 << 22  # sampled positions per flat buffer: 2 x 16 MB of float32
+DUMP_SEED = 20240229
+
+
+def dump_outputs(dirname, model, loss):
+    """What the caller of the last timed step holds after it: the step's loss, and the updated parameters
+    and that step's gradients at DUMP_SAMPLE fixed positions (seeded, sorted, drawn with replacement) of the
+    flat fp32 buffers.  One float32 .npy per array; returns {name: shape} for the result line."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    n = model.trainable_numel()
+    g = torch.Generator(device="cpu").manual_seed(DUMP_SEED)
+    idx = torch.randint(0, n, (min(DUMP_SAMPLE, n),), generator=g).sort().values
+    idx = idx.to(model.flat_params().device)
+    arrays = {"loss": loss.detach().reshape(1),
+              "params": model.flat_params()[:n].detach()[idx],
+              "grads": model.flat_grads()[:n].detach()[idx]}
+    shapes = {}
+    for name, t in arrays.items():
+        a = t.to(torch.float32).cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes
+
+
+def full_report(args, res, model, opt, reducer, runner, eager_step, batch, dev, rank, world, dp, ranks_seen):
+    """--full: what the run measures and checks beside the headline figure, added to ``res`` (rank 0):
+    per-kernel roofline, the DP exchange's exposed time, the fresh-batch loop, parameter checksums."""
+    from repurpose_amd import kernels as K
+    B, T = args.batch, args.seq_len
+    value = res["value"]
     # per-kernel durations: the same kernels on the same data, timed with HIP events on their launch
     # stream over eager steps right after the timed region (a graph replay carries no per-launch
     # events, and ~100 event pairs per eager step would themselves add ~0.6 ms to the timed steps)
@@ -320,7 +407,6 @@ def main():
         waits = [a.elapsed_time(b) for a, b in reducer.timing]
         reducer.timing = None
     kern_ms = {n: v[0] for n, v in kern.items()}
-    value = world * B * T * args.steps / elapsed
 
     fresh = None
     if (world == 1 and not args.no_fresh_batch) or args.fresh_batch:
@@ -335,82 +421,55 @@ def main():
         dist.all_gather_object(allc, csum)
         checksums = allc
         dist.barrier()
-
-    if rank == 0:
-        fpt = flops_per_timestep(T)
-        H, dk = 8, 64
-        peak = PEAK_BF16_TFLOPS if args.dtype == "bf16" else PEAK_FP32_TFLOPS
-        traffic = pmc_traffic(B, T)
-        # where the step runs the two-role backward (config 4) the dQ / dK/dV kernels never run alone:
-        # the roofline then names the launch the step does run
-        rk = args.roofline_kernel
-        if kern_ms.get(rk) is None and kern_ms.get("attn_bwd_roles") is not None and rk.startswith("attn_bwd"):
-            rk = "attn_bwd_roles"
-        roof = roofline_of(rk, kern_ms, B, T, peak, traffic)
-        roof["step_tflops"] = fpt * value / world / 1e12
-        roof["step_frac"] = roof["step_tflops"] / peak
-        roof["other_kernels"] = [roofline_of(n, kern_ms, B, T, peak, traffic) for n in KERNEL_FLOPS
-                                 if n != rk and kern_ms.get(n) is not None]
-        # the weight-gradient GEMMs (every Linear's dW = dY^T X + bias gradient, grouped or split-K):
-        # algorithmic 2*N*K*T per launch summed over the timed launches
-        avg, n_l, tot, fl, _ = kern["gemm_wgrad"]
-        if n_l and fl:
-            ach = fl / (tot * 1e-3) / 1e12
-            roof["other_kernels"].append({"kernel": "gemm_wgrad (all shapes)", "bound": "mfma", "achieved": ach,
-                                          "peak": peak,
-                                          "unit": "TFLOP/s", "launches_per_step": n_l / kern_steps,
-                                          "ms_per_step": tot / kern_steps, "avg_launch_ms": avg,
-                                          "frac": ach / peak})
-        roof["kernel_timing"] = "HIP events on the launch stream over %d eager steps after the timed region" % kern_steps
-        res = {"metric": METRIC, "value": value,
-               "unit": "feature-timesteps/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-               "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-               "vs_baseline": None, "dtype": args.dtype, "data": "synthetic (seeded, SURVEY §8d statistics)",
-               "config": {"workload": f"tri-modal MMCTransformer L=16 d=512 H=8 dff=2048, T={T}, B={B}/GPU, "
-                                      f"train step fwd+focal+bwd+allreduce+Adam",
-                          "model": "MMCTransformer (configs/Repurpose.yaml)", "global_batch": B * world,
-                          "seq_len": T, "parallelism": f"dp{world}"},
-               "loss": loss_val, "roofline": roof, "ranks_seen": ranks_seen,
-               "timing": "mean ms over the K timed steps (barrier + synchronize on both sides, max over ranks)",
-               "param_checksums": checksums,
-               "rank_ms_per_step": [x / args.steps * 1e3 for x in per_rank],
-               "rank_spread_ms": (max(per_rank) - min(per_rank)) / args.steps * 1e3,
-               "execution": ("hip-graph replay of the captured step" + (" (RCCL all-reduces captured)" if dp else ""))
-               if use_graph else "eager (per-launch)"}
-        if dp:
-            # where the DP step's time goes: the step stream's stalls on the bucket waits (the exchange not
-            # hidden behind the backward), the weight-gradient launches of one step in issue order (the
-            # grouped launch cut at each full round of tiles so early buckets' exchange overlaps the rest)
-            _, n_w, _, _, each_w = kern["gemm_wgrad"]
-            per = n_w // kern_steps if n_w else 0
-            res["comm"] = {"backend": reducer.backend, "bucket_mb": reducer.bucket_elems * 4 / 2 ** 20,
-                           "allreduce_bytes_per_step": model.trainable_numel() * 4,
-                           "buckets_per_step": len(waits) // kern_steps if waits else 0,
-                           "exposed_ms": sum(waits) / kern_steps if waits else None,
-                           "max_bucket_wait_ms": max(waits) if waits else None,
-                           "wgrad_launch_ms": each_w[-per:] if per else [],
-                           "adam": "per bucket after its wait" if reducer.on_bucket is not None else "whole buffer",
-                           "timing": "HIP events on the step stream around each bucket's wait, eager steps "
-                                     "after the timed region"}
-        # SURVEY §8d reports the optimizer step separately: `value` includes it (whole train step)
-        if kern.get("adam") and kern["adam"][0]:
-            res["optimizer_ms_per_step"] = kern["adam"][2] / kern_steps
-            res["ms_per_step_excl_optimizer"] = res["ms_per_step"] - res["optimizer_ms_per_step"]
-        if fresh is not None:
-            res["fresh_batch"] = fresh
-    if world == 1 and not args.no_parity_mode and args.dtype != "fp32":
-        del runner, model, opt, batch
-        torch.cuda.empty_cache()
-        pm = parity_mode(B, T, dev, rank)
-        if rank == 0:
-            res["parity_mode"] = pm
-    if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
-            res["cpu_baseline"] = cpu_baseline(T)
-            res["speedup_vs_cpu"] = value / res["cpu_baseline"]["value"]
-        print(json.dumps(res), flush=True)
+    if rank != 0:
+        return
+    fpt = flops_per_timestep(T)
+    peak = PEAK_BF16_TFLOPS if args.dtype == "bf16" else PEAK_FP32_TFLOPS
+    traffic = pmc_traffic(B, T)
+    # where the step runs the two-role backward (config 4) the dQ / dK/dV kernels never run alone:
+    # the roofline then names the launch the step does run
+    rk = args.roofline_kernel
+    if kern_ms.get(rk) is None and kern_ms.get("attn_bwd_roles") is not None and rk.startswith("attn_bwd"):
+        rk = "attn_bwd_roles"
+    roof = roofline_of(rk, kern_ms, B, T, peak, traffic)
+    roof["step_tflops"] = fpt * value / world / 1e12
+    roof["step_frac"] = roof["step_tflops"] / peak
+    roof["other_kernels"] = [roofline_of(n, kern_ms, B, T, peak, traffic) for n in KERNEL_FLOPS
+                             if n != rk and kern_ms.get(n) is not None]
+    # the weight-gradient GEMMs (every Linear's dW = dY^T X + bias gradient, grouped or split-K):
+    # algorithmic 2*N*K*T per launch summed over the timed launches
+    avg, n_l, tot, fl, _ = kern["gemm_wgrad"]
+    if n_l and fl:
+        ach = fl / (tot * 1e-3) / 1e12
+        roof["other_kernels"].append({"kernel": "gemm_wgrad (all shapes)", "bound": "mfma", "achieved": ach,
+                                      "peak": peak,
+                                      "unit": "TFLOP/s", "launches_per_step": n_l / kern_steps,
+                                      "ms_per_step": tot / kern_steps, "avg_launch_ms": avg,
+                                      "frac": ach / peak})
+    roof["kernel_timing"] = "HIP events on the launch stream over %d eager steps after the timed region" % kern_steps
+    res["roofline"] = roof
+    res["param_checksums"] = checksums
     if dp:
-        dist.destroy_process_group()
+        # where the DP step's time goes: the step stream's stalls on the bucket waits (the exchange not
+        # hidden behind the backward), the weight-gradient launches of one step in issue order (the
+        # grouped launch cut at each full round of tiles so early buckets' exchange overlaps the rest)
+        _, n_w, _, _, each_w = kern["gemm_wgrad"]
+        per = n_w // kern_steps if n_w else 0
+        res["comm"] = {"backend": reducer.backend, "bucket_mb": reducer.bucket_elems * 4 / 2 ** 20,
+                       "allreduce_bytes_per_step": model.trainable_numel() * 4,
+                       "buckets_per_step": len(waits) // kern_steps if waits else 0,
+                       "exposed_ms": sum(waits) / kern_steps if waits else None,
+                       "max_bucket_wait_ms": max(waits) if waits else None,
+                       "wgrad_launch_ms": each_w[-per:] if per else [],
+                       "adam": "per bucket after its wait" if reducer.on_bucket is not None else "whole buffer",
+                       "timing": "HIP events on the step stream around each bucket's wait, eager steps "
+                                 "after the timed region"}
+    # SURVEY §8d reports the optimizer step separately: `value` includes it (whole train step)
+    if kern.get("adam") and kern["adam"][0]:
+        res["optimizer_ms_per_step"] = kern["adam"][2] / kern_steps
+        res["ms_per_step_excl_optimizer"] = res["ms_per_step"] - res["optimizer_ms_per_step"]
+    if fresh is not None:
+        res["fresh_batch"] = fresh
 
 
 PMC_TRAFFIC_FILES = ("r06_pmc_traffic.json", "r06_pmc_traffic_T4096_B1.json", "r06_pmc_traffic_T1024_B8.json")

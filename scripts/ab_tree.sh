@@ -2,7 +2,7 @@
 # Same-box A/B of the training step between two source trees (A = $1, e.g. a git worktree of an
 # older commit built in place; B = this tree), interleaved N times.
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
-A=$1; N=${2:-3}; ARGS=${3:-"--steps 10 --warmup 3 --no-cpu-baseline"}
+A=$1; N=${2:-3}; ARGS=${3:-"--full --steps 10 --warmup 3 --no-cpu-baseline"}
 mkdir -p gpurun_out
 for i in $(seq 1 $N); do
   for v in A B; do

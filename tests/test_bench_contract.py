@@ -48,6 +48,57 @@ def test_gpus_n_launches_n_ranks_as_a_child():
     assert cmd[i + 1:] == ["--gpus", "8", "--steps", "7", "--warmup", "2"]  # --dry-run is not forwarded
 
 
+def test_full_and_dump_outputs_are_options_and_reach_the_ranks():
+    r = _run(["--gpus", "2", "--steps", "4", "--full", "--dump-outputs", "somewhere", "--dry-run"])
+    assert r.returncode == 0, r.stderr
+    cmd = json.loads(r.stdout.strip().splitlines()[-1])["launch"]
+    i = cmd.index(os.path.join(ROOT, "bench.py"))
+    assert cmd[i + 1:] == ["--gpus", "2", "--steps", "4", "--full", "--dump-outputs", "somewhere"]
+
+
+def test_dump_outputs_writes_a_fixed_float32_sample(tmp_path):
+    """dump_outputs(): loss, and the parameters and gradients at the same seeded positions on every call,
+    as float32 .npy files well under 64 MB together."""
+    import numpy as np
+    import torch
+    b = _bench()
+
+    class Flat:
+        def __init__(self, n, pad=8):
+            self.n = n
+            self.p = torch.arange(n + pad, dtype=torch.float32)
+            self.g = -2.0 * torch.arange(n + pad, dtype=torch.float32)
+
+        def trainable_numel(self):
+            return self.n
+
+        def flat_params(self):
+            return self.p
+
+        def flat_grads(self):
+            return self.g
+
+    n = 3 * b.DUMP_SAMPLE + 5  # larger than the sample: a subset is written
+    m = Flat(n)
+    shapes = b.dump_outputs(str(tmp_path / "a"), m, torch.tensor(1.5, dtype=torch.float64))
+    b.dump_outputs(str(tmp_path / "b"), m, torch.tensor(1.5, dtype=torch.float64))
+    assert sorted(os.listdir(tmp_path / "a")) == ["grads.npy", "loss.npy", "params.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 64 * 2 ** 20
+    a = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in ("loss", "params", "grads")}
+    assert shapes == {k: list(v.shape) for k, v in a.items()}
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert a["loss"].tolist() == [1.5] and a["params"].shape == (b.DUMP_SAMPLE,)
+    # params hold their own positions here: inside the trained range, spread over it, grads at the same ones
+    pos = a["params"]
+    assert pos.min() >= 0 and pos.max() < n and pos.max() - pos.min() > 0.9 * n
+    assert np.array_equal(a["grads"], -2.0 * pos)
+    for k in a:
+        assert np.array_equal(a[k], np.load(tmp_path / "b" / (k + ".npy")))
+    # a buffer smaller than the sample is sampled at as many positions as it has
+    small = b.dump_outputs(str(tmp_path / "c"), Flat(1000), torch.tensor(0.0))
+    assert small["params"] == [1000]
+
+
 def test_gpus_must_match_world_size_under_a_launcher():
     r = _run(["--gpus", "4", "--steps", "1"], env={"WORLD_SIZE": "2", "RANK": "0", "LOCAL_RANK": "0"})
     assert r.returncode != 0 and "--gpus 4 but WORLD_SIZE=2" in r.stderr

@@ -2,8 +2,8 @@
 (main.py:139 MMCTransformer(**cfg['model']), :69 MultiGPUStrategy(**cfg['distributed']),
 :190-191 Adam(lr, weight_decay from cfg['train']), :674 inference_(batch, cfg['test_cfg'])).
 
-CPU test: reads the reference's config file in place when the reference tree is present (this
-container; the GPU box has no /root/reference and skips), with yaml.safe_load (the file is plain
+CPU test: reads the unchanged copy of the reference's config file kept as a fixture
+(tests/golden/Repurpose.yaml, settings only), with yaml.safe_load (the file is plain
 YAML; the reference's FullLoader would execute nothing more on it).  The inference settings every GPU
 test uses (tests/test_infer_gpu.py, scripts/val_atiou.py) are checked equal to the file's test_cfg,
 so the GPU parity runs exercise the shipped settings."""
@@ -19,14 +19,12 @@ from repurpose_amd.distributed import MultiGPUStrategy
 from repurpose_amd.MMCTransformer import MMCTransformer
 from repurpose_amd.optim import FusedAdam
 
-CFG_PATH = "/root/reference/configs/Repurpose.yaml"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CFG_PATH = os.path.join(ROOT, "tests", "golden", "Repurpose.yaml")
 
 
 @pytest.fixture(scope="module")
 def cfg():
-    if not os.path.exists(CFG_PATH):
-        pytest.skip("reference tree not present (GPU box)")
     with open(CFG_PATH) as f:
         return yaml.safe_load(f)
 

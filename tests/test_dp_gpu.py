@@ -1,7 +1,7 @@
 """The data-parallel step as the driver's multi-GPU bench runs it (config 3: DDP over RCCL,
-``/root/reference/utils/distributed.py:415-428`` around ``main.py:331-386``), on the one-GPU box:
+the reference's ``utils/distributed.py:415-428`` around ``main.py:331-386``), on the one-GPU box:
 
-* ``bench.py --gpus 2`` end to end: the launcher starts two ranks (gloo: RCCL refuses two ranks on one
+* ``bench.py --gpus 2 --full`` end to end: the launcher starts two ranks (gloo: RCCL refuses two ranks on one
   device), each runs the eager DP step with the bucketed all-reduce; one JSON line, ``n_gpus`` and
   ``ranks_seen`` 2, a finite loss and bitwise identical parameters on both ranks after the last step;
 * the all-reduce buckets of every weight-gradient schedule the DP backward can take (the default
@@ -15,7 +15,7 @@
   whole-buffer update in eager DP steps, here and on two gloo ranks;
 * the DP update pinned to the oracle: two ranks through ``MultiGPUStrategy.setup`` / ``wrap_model`` /
   the HIP backward / ``FusedAdam`` against the CPU oracle's gradients of each rank's batch, averaged,
-  then ``torch.optim.Adam`` (``/root/reference/main.py:331-369``, ``utils/distributed.py:415-428``).
+  then ``torch.optim.Adam`` (the reference's ``main.py:331-369``, ``utils/distributed.py:415-428``).
 
 Every process group here is created with a bounded timeout (60 s), so a stuck rendezvous or collective
 raises with a stack instead of stalling the suite, and the parent notices a worker that died without
@@ -100,7 +100,7 @@ def test_bench_two_ranks_gloo(dev, request, tmp_path):
     out, err = tmp_path / "bench.out", tmp_path / "bench.err"
     with open(out, "w") as fo, open(err, "w") as fe:
         proc = subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3",
-                                 "--warmup", "1"], stdout=fo, stderr=fe, text=True, env=env, cwd=ROOT)
+                                 "--warmup", "1", "--full"], stdout=fo, stderr=fe, text=True, env=env, cwd=ROOT)
         t0 = time.time()
         while True:
             try:

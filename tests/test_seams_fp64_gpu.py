@@ -4,7 +4,7 @@ restatement of the op they compute — not only against the unfused HIP kernels 
 * the exchange GEMM + LayerNorm seams (rp_gemm_ln_fwd / rp_gemm_ln_bwd on 128 x 128 tiles, and forced
   onto the 64- and 32-row exchange tiles): ``y = dropout(x W^T + b) + residual``, ``h = LayerNorm(y)``
   (reference: nn.TransformerEncoderLayer's out_proj / linear2 + dropout + residual + norm,
-  /root/reference/models/MMCTransformer.py:41-55), and the backward's dh = dY W, LayerNorm backward,
+  its models/MMCTransformer.py:41-55), and the backward's dh = dY W, LayerNorm backward,
   residual-gradient add, masked bf16 copy and gamma / beta gradients;
 * the d_ff = 2048 GEMMs on the 256-row phased kernel (linear1 forward with ReLU + dropout, linear2
   dgrad gated by the saved activation);
